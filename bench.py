@@ -7,6 +7,16 @@ per GPU (weak scaling), synthetic CIFAR-shaped data (50,000 train / 10,000 test,
 with fp32 master weights/accumulation, momentum SGD (lr 0.001, m 0.9) every step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--sync step-allreduce|epoch-avg]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up (with the launch / all-reduce A/B
+that picks the timed path), W warmup steps, the K timed steps, the --dump-outputs files, the JSON
+line.  --full adds the other measurement: one complete epoch (train + sync + full test-set
+evaluation: epoch_s, epoch_train_s, eval_s, train_loss, val_loss, val_acc in the JSON line).
+--dump-outputs DIR writes what the timed steps left behind, as a caller of the step path sees it
+after the last timed step: DIR/params.npy and DIR/momentum.npy (fp32 arenas) and DIR/step_stats.npy
+(float64: loss sum, batches, correct, samples since the last statistics reset).  Data, initial weights and
+sample order depend only on the arguments, so two builds can be compared output for output.
 
 Synchronisation defaults to a per-step gradient all-reduce inside the step hipGraph.  At N > 1
 the bench first MEASURES its transport (--allreduce ab, parallel/autotune.py): in the untimed
@@ -78,6 +88,24 @@ def _reserve_stdout() -> int:
     return real
 
 
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: all files of one rank together stay under this
+
+
+def dump_outputs(out_dir: str, rank: int, tensors: dict) -> None:
+    """Write each tensor as ``out_dir/<name>.npy`` (float64 stays float64, everything else becomes
+    float32).  An array over its share of DUMP_MAX_BYTES is cut to a fixed, seeded sample of its
+    elements (sorted indices, the same in every run)."""
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(tensors)) - 4096  # (4096: room for the .npy header)
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy().reshape(-1)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+        if a.nbytes > share:
+            keep = np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if rank else "") + ".npy"), a)
+
+
 def main():
     out_fd = _reserve_stdout()
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -115,7 +143,13 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"],
                     help="bf16: bf16 MFMA operands, fp32 accumulation / master weights (lenet_fused.hip); fp32: "
                          "fp32 operands throughout, the reference's arithmetic (lenet_f32.hip)")
-    ap.add_argument("--no-epoch", action="store_true", help="skip the full-epoch timing")
+    ap.add_argument("--full", action="store_true",
+                    help="also time one complete epoch (train + sync + full test-set evaluation) after the "
+                         "timed window; a plain run measures the timed window only")
+    ap.add_argument("--no-epoch", action="store_true", help="with --full: skip the full-epoch timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the parameters, momentum and step statistics they left "
+                         "as DIR/<name>.npy (ranks > 0: <name>_rank<r>.npy)")
     ap.add_argument("--no-graphs", action="store_true",
                     help="eager launches (needed with DNN_BACKEND=gloo, whose collectives are not capturable)")
     ap.add_argument("--seed", type=int, default=0)
@@ -125,6 +159,7 @@ def main():
                     help="synthetic training-set size (CIFAR-10: 50,000); smaller = more epoch boundaries "
                          "inside the timed window (diagnostic)")
     args = ap.parse_args()
+    epoch_on = args.full and not args.no_epoch  # the full-epoch timing (and the test split it evaluates)
 
     me = [sys.executable, os.path.abspath(__file__)] + sys.argv[1:]
     if args.gpus > 1 and not selflaunch.launcher_present():
@@ -158,7 +193,7 @@ def main():
     B = args.batch_size
 
     train = synthetic(args.train_samples, args.seed, True, noise=args.noise)
-    test = synthetic(10_000, args.seed, False, noise=args.noise)
+    test = synthetic(10_000, args.seed, False, noise=args.noise) if epoch_on else None
     sampler = EpochSampler.for_rank(len(train), comm.rank, comm.world, seed=args.seed, mode="shard")
     if args.model == "lenet" and args.engine in ("auto", "fused"):
         engine = HipEngine(batch=B, seed=args.seed, device=device, graph_chunk=args.graph_chunk,
@@ -167,7 +202,7 @@ def main():
         engine = make_engine(str(device), B, 0.001, 0.9, seed=args.seed, model=args.model, engine="layers",
                              dtype=args.dtype, graph_chunk=min(args.graph_chunk, 16), use_graphs=not args.no_graphs)
     engine.attach(train)
-    test_dev = test.to(device)
+    test_dev = test.to(device) if epoch_on else None
     policy = make_policy(args.sync, comm)
     policy.lazy_check = True  # no per-epoch host sync; the xGMI error word is checked after the run
     policy.record_waits = True  # per-step exchange wait stamps (one store per wave and step)
@@ -183,11 +218,17 @@ def main():
     cur = EpochCursor(engine, sampler, policy, B)
     # first-call costs of the eval path (kernel, D2H, host ops) - before the A/B too: a full-chip
     # kernel, after which the A/B's candidates run on the GPU state the timed window will see
-    if not args.no_epoch:
+    if epoch_on:
         wl, wc = engine.evaluate_samples(test_dev, 0, len(test))
         wl2, wc2 = torch.zeros_like(wl), torch.zeros_like(wc, dtype=torch.float32)
         comm.allreduce_(wl2, "sum")
         eval_metrics(wl + wl2, wc.float() + wc2, B)
+    else:
+        # a plain run has no evaluation, but its window is timed in the same process state: the first
+        # torch kernel, device-to-host copy and host reduction happen here (milliseconds), as the
+        # evaluation's metrics do above (without them a 20/5 window measured 16.4 instead of 16.0 us/step)
+        z = torch.zeros(10_000, device=device)
+        eval_metrics(z, z, B)
     ab = {}
     if comm.distributed and args.sync == "step-allreduce" and args.allreduce == "ab":
         ab_steps, ab_warm = ab_window(cur.steps_per_epoch, args.ab_steps or args.steps, args.warmup)
@@ -272,6 +313,9 @@ def main():
             waits = {k: round(v, 3) for k, v in waits.items()}
         else:
             waits = None
+    if args.dump_outputs:  # (before anything else runs a step: the state the last timed step left)
+        dump_outputs(args.dump_outputs, comm.rank, {"params": engine.master, "momentum": engine.mom,
+                                                    "step_stats": engine.stats})
     for _ in range(args.diag_windows):  # diagnostic only: the reported window is the first one
         comm.barrier()
         torch.cuda.synchronize(device)
@@ -295,7 +339,7 @@ def main():
 
     # one complete epoch from its first step: train + averaging/sync + full test-set eval
     epoch = {}
-    if not args.no_epoch:
+    if epoch_on:
         cur.left = 0
         cur._next_epoch()
         engine.epoch_stats(reset=True)

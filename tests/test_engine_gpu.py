@@ -140,7 +140,7 @@ def test_bench_two_ranks_one_gpu_gloo(tmp_path):
     env = dict(os.environ, PYTHONPATH=ROOT, DNN_BACKEND="gloo", OMP_NUM_THREADS="2")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29677", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "20", "--warmup", "4", "--no-graphs"],
+                        "--gpus", "2", "--steps", "20", "--warmup", "4", "--no-graphs", "--full"],
                        cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -149,6 +149,44 @@ def test_bench_two_ranks_one_gpu_gloo(tmp_path):
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["config"]["parallelism"] == "dp2" and out["config"]["global_batch"] == 128
     assert out["value"] > 0 and out["steps"] == 20 and 0 <= out["val_acc"] <= 100
+
+
+def test_bench_plain_run_dumps_the_timed_steps_outputs(tmp_path):
+    """A plain bench.py run: one JSON line without the --full epoch figures, --steps timed steps,
+    and --dump-outputs files that hold exactly what the warmup + timed steps computed (the same
+    steps of an engine in this process, from the same data, weights and sample order)."""
+    import json
+
+    from distributed_neural_network_amd.data import EpochSampler
+    from distributed_neural_network_amd.data.datasets import SYNTH_NOISE_HARD
+
+    env = dict(os.environ, PYTHONPATH=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--train-samples", "2048", "--launch", "direct", "--dump-outputs", str(tmp_path / "out")],
+                       cwd=tmp_path, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["steps"] == 3 and out["unit"] == "images/s" and out["higher_is_better"] is True and out["dtype"] == "bf16"
+    assert out["ms_per_step"] > 0 and abs(out["value"] * out["ms_per_step"] / 1000.0 - 64) < 0.01 * 64
+    assert "epoch_s" not in out and "val_acc" not in out  # (those are --full's)
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("params", "momentum", "step_stats")}
+    assert got["params"].dtype == np.float32 and got["momentum"].dtype == np.float32
+    assert got["step_stats"].dtype == np.float64
+
+    train = synthetic(2048, 0, True, noise=SYNTH_NOISE_HARD)
+    eng = HipEngine(batch=64, seed=0, device="cuda:0")
+    eng.attach(train)
+    eng.begin_epoch(EpochSampler.for_rank(len(train), 0, 1, seed=0, mode="shard").order(0))
+    eng.prepare_graphs(exact=(3,))
+    eng.run_steps(1)
+    eng.run_steps(3)
+    torch.cuda.synchronize()
+    assert np.array_equal(got["params"], eng.master.cpu().numpy())
+    assert np.array_equal(got["momentum"], eng.mom.cpu().numpy())
+    assert np.array_equal(got["step_stats"], eng.stats.cpu().numpy())
+    assert got["step_stats"][1] == 4 and got["step_stats"][3] == 4 * 64  # warmup + timed batches, their samples
 
 
 @pytest.mark.parametrize("sync", ["step-allreduce", "epoch-avg"])

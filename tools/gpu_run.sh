@@ -19,7 +19,7 @@
 #   winfit           bench --steps 10..160 with --diag-windows (wall vs event time per window)
 #   k20serial | longserial | profserial   the same with the pipelined step off (DNN_PIPELINE=0)
 #   k20pipe | longpipe | profpipe         ... and on (DNN_PIPELINE=1)
-#   long | long32 | long32serial   bench.py default window (5000 / 500), bf16 / fp32 / fp32 without PERS
+#   long | long32 | long32serial   bench.py --full, default window (5000 / 500) + the epoch timing, bf16 / fp32 / fp32 without PERS
 #   b2k              bench.py 2000 / 200 steps, no epoch timing (envb2k:VAR=val: under one env setting)
 #   profk20          rocprofv3 --kernel-trace over the driver's 20/5 window (+3 diagnostic windows)
 #   prof | prof32    rocprofv3 --kernel-trace --stats over 2000 steps (bf16 / fp32)
@@ -78,9 +78,9 @@ for s in "$@"; do
       [ "$rc" -le 1 ] || exit "$rc" ;;
     k20|k20b) timeout -k 10 150 python bench.py --steps 20 --warmup 5 > "$O/$s.json" 2> "$O/$s.err" ;;
     k20pipe) DNN_PIPELINE=1 timeout -k 10 150 python bench.py --steps 20 --warmup 5 > "$O/$s.json" 2> "$O/$s.err" ;;
-    longpipe) DNN_PIPELINE=1 timeout -k 10 300 python bench.py > "$O/$s.json" 2> "$O/$s.err" ;;
+    longpipe) DNN_PIPELINE=1 timeout -k 10 300 python bench.py --full > "$O/$s.json" 2> "$O/$s.err" ;;
     k20serial) DNN_PIPELINE=0 timeout -k 10 150 python bench.py --steps 20 --warmup 5 > "$O/$s.json" 2> "$O/$s.err" ;;
-    longserial) DNN_PIPELINE=0 timeout -k 10 300 python bench.py > "$O/$s.json" 2> "$O/$s.err" ;;
+    longserial) DNN_PIPELINE=0 timeout -k 10 300 python bench.py --full > "$O/$s.json" 2> "$O/$s.err" ;;
     envk20:*)  # the driver's window under one runtime env setting: envk20:VAR=value
       kv="${s#envk20:}"; n=$(echo "$kv" | tr '=/' '__')
       env "$kv" timeout -k 10 150 python bench.py --steps 20 --warmup 5 > "$O/k20_$n.json" 2> "$O/k20_$n.err" ;;
@@ -104,7 +104,7 @@ for s in "$@"; do
     k20f32) timeout -k 10 150 python bench.py --dtype fp32 --steps 20 --warmup 5 > "$O/$s.json" 2> "$O/$s.err" ;;
     k20f32serial) DNN_PERSIST=0 timeout -k 10 150 python bench.py --dtype fp32 --steps 20 --warmup 5 > "$O/$s.json" \
                     2> "$O/$s.err" ;;
-    long) timeout -k 10 300 python bench.py > "$O/long.json" 2> "$O/long.err" ;;
+    long) timeout -k 10 300 python bench.py --full > "$O/long.json" 2> "$O/long.err" ;;
     b2k) timeout -k 10 200 python bench.py --steps 2000 --warmup 200 --no-epoch > "$O/b2k.json" 2> "$O/b2k.err" ;;
     envb2k:*)  # b2k under one runtime env setting: envb2k:VAR=value
       kv="${s#envb2k:}"; n=$(echo "$kv" | tr '=/' '__')
@@ -112,9 +112,9 @@ for s in "$@"; do
     envphasepers:*)  # phasepers under one runtime env setting
       kv="${s#envphasepers:}"; n=$(echo "$kv" | tr '=/' '__')
       env "$kv" timeout -k 10 300 python tools/phase_trace.py --pers > "$O/phasepers_$n.txt" 2>&1 ;;
-    long32) timeout -k 10 300 python bench.py --dtype fp32 > "$O/long32.json" 2> "$O/long32.err" ;;
-    long32serial) DNN_PERSIST=0 timeout -k 10 300 python bench.py --dtype fp32 > "$O/$s.json" 2> "$O/$s.err" ;;
-    long32pers) DNN_PERSIST_F32=1 timeout -k 10 300 python bench.py --dtype fp32 > "$O/$s.json" 2> "$O/$s.err" ;;
+    long32) timeout -k 10 300 python bench.py --full --dtype fp32 > "$O/long32.json" 2> "$O/long32.err" ;;
+    long32serial) DNN_PERSIST=0 timeout -k 10 300 python bench.py --full --dtype fp32 > "$O/$s.json" 2> "$O/$s.err" ;;
+    long32pers) DNN_PERSIST_F32=1 timeout -k 10 300 python bench.py --full --dtype fp32 > "$O/$s.json" 2> "$O/$s.err" ;;
     k20f32pers) DNN_PERSIST_F32=1 timeout -k 10 150 python bench.py --dtype fp32 --steps 20 --warmup 5 > "$O/$s.json" \
                   2> "$O/$s.err" ;;
     prof|prof32|profserial|profpipe)
